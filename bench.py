@@ -10,7 +10,9 @@ gather of the audio to rank 0 (DDSPP_BENCH_GATHER=all: to every rank).
 
 Workload at N GPUs (weak scaling): BASELINE.json config 3 per GPU = 64 segments x 3 s, poly=16,
 24 kHz, 250 Hz controls, maestro-v2 dims (H=128 harmonics, K=96 noise bands, S=1), 3 s reverb IR;
-8 GPUs x 64 = the batch=512 of config 4.  The JSON line also carries
+8 GPUs x 64 = the batch=512 of config 4.  A plain run only sets up, warms up, times the K steps and prints the line
+(`value`, `ms_per_step`, `step_ms`); --dump-outputs DIR also writes what the last timed step returned to its caller
+(dump_outputs).  With --full the JSON line also carries
   * roofline       : the operator-boundary cos_oscillator_bank kernel (8 B read per
                      oscillator-sample + 4 B written per sample) timed with HIP events on materialised
                      [rows, N, H] envelopes of the same workload, against 8 TB/s;
@@ -22,7 +24,7 @@ Workload at N GPUs (weak scaling): BASELINE.json config 3 per GPU = 64 segments 
                      multiply-adds (samples x taps) and of all its VALU instructions (counts from profiles/);
   * cpu_baseline   : the float32-faithful numpy restatement (oracle/, the only runnable stand-in for the
                      TF/ddsp reference here) and an op-by-op torch-CPU version on all cores, timed on this host;
-  * value          : global batch x samples / MEDIAN of the per-step device times (every step bracketed by HIP events
+  * value          : (every run) global batch x samples / MEDIAN of the per-step device times (every step bracketed by HIP events
                      on the launch stream and synchronised; with N > 1 the step includes its gather, max over ranks)
                      -- SURVEY.md 8(d)'s definition.  `pipelined` holds the wall clock of K back-to-back steps (barrier +
                      synchronize on both sides, max over ranks), where the side stream / the gather of one step overlap
@@ -30,7 +32,7 @@ Workload at N GPUs (weak scaling): BASELINE.json config 3 per GPU = 64 segments 
   * roofline.measured_peak : device copy / triad / read rates measured in the same run, next to the 8 TB/s spec;
   * counters_stale : true when profiles/step_valu.json / osc_traffic.json describe another build of the kernels
                      (their csrc hash differs): frac_mix / traffic are then dropped;
-  * step_ms        : per-step HIP-event times (median / min / max) of the headline call;
+  * step_ms        : (every run) per-step HIP-event times (median / min / max) of the headline call;
   * sustained      : >= 5 s of back-to-back headline steps (one HIP event per step, no synchronisation inside), the median
                      of the LAST HALF of the per-step times, with the shader clock and the socket power sampled meanwhile
                      (round 5: the K timed steps are 30 ms of GPU time -- this is what the step costs once power and
@@ -40,11 +42,11 @@ Workload at N GPUs (weak scaling): BASELINE.json config 3 per GPU = 64 segments 
     shipped_configs (every gin file of the reference; the ENSTDkCl rows with the FDN impulse response kept AND designed per
     call): other call forms / inputs.  --extras full adds the hipGraph / one-call-driver forms of a single stream, the
     whole-file renders (136 s, 20 min) and the torch-CPU leg of cpu_baseline; --extras none drops them all;
-  * phase_seconds  : wall clock of the sections of this script (the default run is sized to finish in well under a minute
+  * phase_seconds  : wall clock of the sections of this script (the --full run is sized to finish in well under a minute
                      after `import torch`, so that the driver's GPU-busy sampler sees the GPU at work);
   * with N > 1: per_rank (every rank's own median step and pipelined step), gather_to_rank0 / allgather alone, and
     gather_hidden (pipelined step against the synchronised one minus the collective: does the async gather hide?).
-Launch: python bench.py [--gpus N --steps K --warmup W].  With N > 1 and no torchrun environment the script
+Launch: python bench.py [--gpus N --steps K --warmup W] [--full] [--dump-outputs DIR].  With N > 1 and no torchrun environment the script
 starts the N ranks itself (torch.distributed.run, one process per GPU) and fails loudly when the box has fewer
 than N GPUs.
 """
@@ -65,6 +67,8 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
+DUMP_BUDGET_BYTES = 60_000_000   # --dump-outputs: array data of all files; with the .npy headers well under 64 MB
+DUMP_SEED = 20240
 HBM_PEAK_BYTES = 8.0e12          # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
 N_SIMDS = 1024                   # 256 CUs x 4 SIMDs
 VALU_CYCLES_PER_WAVE_INST = 2    # a wave64 VALU instruction issues over 2 cycles on a SIMD-32 (MI355X_MICROARCH.md)
@@ -97,6 +101,13 @@ def parse(argv=None):
     ap.add_argument('--sustain-seconds', type=float, default=5.0,
                     help='length of the `sustained` measurement (0: skip)')
     ap.add_argument('--cpu-voices', type=int, default=16)
+    ap.add_argument('--full', action='store_true',
+                    help='measure everything besides the headline steps: graded kernel and step rooflines, pipelined and '
+                         'sustained steps, collectives alone, extras, CPU baseline (the options above choose among them; '
+                         'a run without --full times the headline steps only)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write the arrays the last one returned to its caller as DIR/<name>.npy '
+                         '(float32 / float64, a seeded sample of every array when they exceed 64 MB in all)')
     return ap.parse_args(argv)
 
 
@@ -342,25 +353,78 @@ def time_steps(fn, steps, warmup, dist=None, drain=None):
     return time.perf_counter() - t0
 
 
-def event_times(fn, reps, warmup=2):
-    """Per-call device times (ms) of fn on torch's current stream (the library launches there), HIP events."""
+def event_times(fn, reps, warmup=2, keep_last=False):
+    """Per-call device times (ms) of fn on torch's current stream (the library launches there), HIP events.
+    keep_last: return (times, what the last call returned); every earlier result is dropped before the next call."""
     for _ in range(warmup):
         fn()
     torch.cuda.synchronize()
     stream = torch.cuda.current_stream()
     ts = []
+    last = None
     for _ in range(reps):
+        last = None
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record(stream)
-        fn()
+        last = fn()
         e1.record(stream)
         e1.synchronize()
         ts.append(e0.elapsed_time(e1))
-    return ts
+    return (ts, last) if keep_last else ts
 
 
 def ms_summary(ts):
     return {'median': float(np.median(ts)), 'min': float(np.min(ts)), 'max': float(np.max(ts)), 'n': len(ts)}
+
+
+def caller_arrays(result, inputs):
+    """The arrays a caller receives from one call, by their path in the result ('signal',
+    'controls.additive.controls.f0_hz', ...): no input tensor (ddsp's outputs dict echoes the features) and no array
+    twice (the dict names the same tensor under several keys; the first name is kept)."""
+    def key(t):
+        return (t.data_ptr(), tuple(t.shape), t.stride(), t.dtype)
+
+    seen = {key(t) for t in inputs.values() if torch.is_tensor(t)}
+    out = {}
+
+    def walk(prefix, x):
+        if torch.is_tensor(x):
+            if key(x) not in seen:
+                seen.add(key(x))
+                out[prefix] = x
+        elif isinstance(x, dict):
+            for k, v in x.items():
+                walk(f'{prefix}.{k}' if prefix else str(k), v)
+    walk('' if isinstance(result, dict) else 'signal', result)
+    return out
+
+
+def dump_outputs(arrays, out_dir, budget=DUMP_BUDGET_BYTES, seed=DUMP_SEED):
+    """Write every array as out_dir/<name>.npy: floating point as float32 (float64 stays), anything else as float64.
+    When the arrays hold more than `budget` bytes in all, every one is replaced by the same fraction of its elements,
+    flattened, at indices drawn from a generator seeded by `seed` (sorted; the same for every array of the same size).
+    Returns {name: {'shape': full shape, 'sampled': elements kept or None}}."""
+    def as_out(t):
+        t = t.detach()
+        return t if t.dtype in (torch.float32, torch.float64) else t.to(torch.float32 if t.is_floating_point() else torch.float64)
+
+    arrays = {k: as_out(v) for k, v in arrays.items()}
+    total = sum(t.numel() * t.element_size() for t in arrays.values())
+    frac = min(1.0, budget / total) if total else 1.0
+    os.makedirs(out_dir, exist_ok=True)
+    index, draws = {}, {}                # draws: element count -> sampled indices (a draw depends on nothing else)
+    for name, t in arrays.items():
+        kept = None
+        if frac < 1.0:
+            n = t.numel()
+            if n not in draws:
+                draws[n] = torch.randperm(n, generator=torch.Generator().manual_seed(seed))[:max(1, int(n * frac))].sort().values
+            kept = draws[n].numel()
+            t = t.reshape(-1)[draws[n].to(t.device)]
+        fname = ''.join(c if c.isalnum() or c in '._-' else '_' for c in name)
+        np.save(os.path.join(out_dir, fname + '.npy'), t.cpu().numpy())
+        index[fname] = {'shape': list(arrays[name].shape), 'sampled': kept}
+    return index
 
 
 class GpuSampler:
@@ -758,8 +822,8 @@ def measure_roofline_noise(dp, base, args, T, U, device, ceiling=None):
 
 
 def measure_cpu_baseline(args, T, U, full=False):
-    """(full=False, the default run: the numpy oracle on 32 threads only, ~6 s; full=True adds a second thread count and the
-    torch-CPU leg, whose 256-thread probe alone is half a minute on the GPU box's host.)
+    """(full=False, `--full`: the numpy oracle on 32 threads only, ~6 s; full=True adds a second thread count and the
+    torch-CPU leg (`--full --extras full`), whose 256-thread probe alone is half a minute on the GPU box's host.)
     The oracle (float32-faithful numpy restatement of the TF/ddsp reference -- TF itself cannot be
     installed here) on a bounded sample of the same workload: whole 3 s, poly-16 segments, one
     thread per voice task, sized for roughly 10 s of wall clock on this host; and the op-by-op torch-CPU
@@ -822,7 +886,7 @@ def measure_cpu_baseline(args, T, U, full=False):
         out = dict(numpy_port)
         out['numpy_oracle'] = numpy_port
         out['note'] = ('TensorFlow / ddsp are not installable on this host: the float32-faithful numpy restatement of the '
-                       'reference chain stands in (bench.py --extras full adds the op-by-op torch-CPU chain)')
+                       'reference chain stands in (bench.py --full --extras full adds the op-by-op torch-CPU chain)')
         return out
     # torch-CPU: whole segments through the vectorised operator sequence, intra-op pool on all cores (and on 32, where
     # oversubscribing tiny ops hurts less; the faster of the two is reported).  Bounded: a probe on one voice x 0.5 s
@@ -913,7 +977,8 @@ def main():
     import ddsp_piano_amd as dp
     from ddsp_piano_amd import parallel
 
-    extras_level = 'none' if args.no_extras else args.extras
+    # without --full only the headline steps run: every other measurement below is gated on it
+    extras_level = ('none' if args.no_extras else args.extras) if args.full else 'none'
     phase_s, _t_phase = {}, [time.perf_counter()]
 
     def phase_done(name):
@@ -933,7 +998,7 @@ def main():
     # the sections below reads 1.5 % slower (tools/roofline_order.py, four alternating pairs: 0.726-0.737 of 8 TB/s fresh
     # against 0.717-0.726 late; DESIGN.md section 4a: the rate is a property of where the process's buffers lie).
     roof = None
-    if rank == 0 and not args.no_roofline:
+    if rank == 0 and args.full and not args.no_roofline:
         roof = measure_roofline(dp, base, args, T, U, device)
     phase_done('inputs_and_graded_kernel')
     pg = build_group(dp, P, sr)
@@ -950,10 +1015,14 @@ def main():
             state['work'].wait()
             state['work'] = None
 
-    def call(group, f):
+    def result(group, f):              # what the caller of the timed path receives
         if want_dict:
-            return group(f, return_outputs_dict=True)['signal']        # piano_model.py:160-164
+            return group(f, return_outputs_dict=True)                   # piano_model.py:160-164
         return group(f)
+
+    def call(group, f):
+        r = result(group, f)
+        return r['signal'] if want_dict else r
 
     def step():
         audio = call(pg, feats)
@@ -970,10 +1039,10 @@ def main():
     #     overlaps its neighbours.  With N > 1 a step includes its own gather (synchronous).  value = global samples /
     #     the MEDIAN step time, max over ranks ("device-synchronised, median of >= 20 runs").
     def sync_step():
-        audio = call(pg, feats)
+        out = result(pg, feats)
         if use_dist:
-            parallel.gather_audio(audio, gathered[0], dst=gather_dst)
-        return audio
+            parallel.gather_audio(out['signal'] if want_dict else out, gathered[0], dst=gather_dst)
+        return out
 
     for _ in range(args.warmup):
         sync_step()
@@ -981,7 +1050,7 @@ def main():
         dist.barrier()
     torch.cuda.synchronize()
     t_wall0 = time.perf_counter()
-    step_ts = event_times(sync_step, args.steps, warmup=0)
+    step_ts, last_out = event_times(sync_step, args.steps, warmup=0, keep_last=True)
     torch.cuda.synchronize()
     if dist is not None:
         dist.barrier()
@@ -992,26 +1061,33 @@ def main():
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         med, wall_sync = float(tt[0].item()), float(tt[1].item())
     value = world * B * N / med
-    # (2) the same K steps back to back (barrier + synchronize on both sides, max over ranks): the side stream and the
-    #     gather of one step overlap the next step's kernels -- what a caller that keeps the GPU fed gets
-    dt = time_steps(step, args.steps, args.warmup, dist, drain if use_dist else None)
-    if use_dist:
-        tt = torch.tensor([dt], dtype=torch.float64, device=device)
-        dist.all_reduce(tt, op=dist.ReduceOp.MAX)
-        dt = float(tt.item())
-
-    extra = {'pipelined': {'ms_per_step': dt / args.steps * 1e3, 'value': world * B * N * args.steps / dt,
-                           'note': f'wall clock of {args.steps} back-to-back steps (barrier + synchronize on both sides, max '
-                                   'over ranks); steps overlap at their edges'},
-             'synchronised_wall_ms_per_step': wall_sync / args.steps * 1e3}
+    extra = {'synchronised_wall_ms_per_step': wall_sync / args.steps * 1e3}
+    if args.dump_outputs and rank == 0:
+        # what this rank's caller got from the last timed step; with N > 1 also the gathered audio of the global batch
+        arrays = caller_arrays(last_out, feats)
+        if use_dist:
+            arrays['gathered_signal'] = gathered[0]
+        extra['dump_outputs'] = {'dir': args.dump_outputs, 'arrays': dump_outputs(arrays, args.dump_outputs)}
+    del last_out
     if use_dist:
         extra['backend'] = backend
+        extra['gather'] = 'all ranks (all_gather_into_tensor)' if gather_dst is None else 'to rank 0 (dist.gather)'
         if share_gpu:
             extra['shared_gpu'] = True           # a dry run of the multi-rank flow, not a multi-GPU measurement
-    if use_dist:
+    if args.full:
+        # (2) the same K steps back to back (barrier + synchronize on both sides, max over ranks): the side stream and the
+        #     gather of one step overlap the next step's kernels -- what a caller that keeps the GPU fed gets
+        dt = time_steps(step, args.steps, args.warmup, dist, drain if use_dist else None)
+        if use_dist:
+            tt = torch.tensor([dt], dtype=torch.float64, device=device)
+            dist.all_reduce(tt, op=dist.ReduceOp.MAX)
+            dt = float(tt.item())
+        extra['pipelined'] = {'ms_per_step': dt / args.steps * 1e3, 'value': world * B * N * args.steps / dt,
+                              'note': f'wall clock of {args.steps} back-to-back steps (barrier + synchronize on both sides, '
+                                      'max over ranks); steps overlap at their edges'}
+    if args.full and use_dist:
         # the collectives by themselves (synchronous), max over ranks: what the overlap has to hide
         audio = call(pg, feats)
-        extra['gather'] = 'all ranks (all_gather_into_tensor)' if gather_dst is None else 'to rank 0 (dist.gather)'
         for name, dst in (('gather_to_rank0', 0), ('allgather', None)):
             ts = []
             for _ in range(5):
@@ -1036,7 +1112,7 @@ def main():
                            'note': 'the collective alone, synchronous (median of 5, max over ranks)'}
     if rank == 0:
         extra['step_ms'] = ms_summary(step_ts)   # the timed steps themselves (this rank)
-    if use_dist:
+    if args.full and use_dist:
         # every rank's own view, and whether the asynchronous gather hides under the next step's kernels (DESIGN.md
         # section 8's open question): compute_only = the step without any collective, on this rank
         comp_ts = event_times(lambda: call(pg, feats), args.steps, warmup=2)
@@ -1058,7 +1134,7 @@ def main():
                                           'step i + 1 synthesises, two landing buffers) costs no more than the step without any '
                                           'collective (+ 3 %)'}
     phase_done('timed_steps_and_collectives')
-    if args.sustain_seconds > 0:
+    if args.full and args.sustain_seconds > 0:
         sus = measure_sustained(step, args.sustain_seconds, med * 1e3, dev_index, world * B * N, sr, drain if use_dist else None)
         if use_dist:
             tt = torch.tensor([sus['ms_per_step']], dtype=torch.float64, device=device)
@@ -1255,7 +1331,7 @@ def main():
         torch.cuda.empty_cache()
         phase_done('extras_whole_file')
     roof_step = roof_noise = None
-    if rank == 0 and not args.no_roofline:
+    if rank == 0 and args.full and not args.no_roofline:
         del feats
         torch.cuda.empty_cache()
         ceiling = measure_valu_ceiling(device)
@@ -1263,7 +1339,7 @@ def main():
         roof_noise = measure_roofline_noise(dp, base, args, T, U, device, ceiling)
         phase_done('roofline_step_and_noise')
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         cpu = measure_cpu_baseline(args, T, U, full=(extras_level == 'full'))
         phase_done('cpu_baseline')
     if dist is not None:
@@ -1289,7 +1365,7 @@ def main():
                                                                                        + (' + one gather of the audio per step (inside the timed step; overlapped with the next step in `pipelined`)' if world > 1 else '')},
             'roofline': roof, 'roofline_step': roof_step, 'roofline_noise': roof_noise, 'cpu_baseline': cpu,
             'counters_stale': (any(bool(x) for x in stale) if stale else None),
-            'extras': extras_level, 'phase_seconds': {k: round(v, 2) for k, v in phase_s.items()},
+            'full': args.full, 'extras': extras_level, 'phase_seconds': {k: round(v, 2) for k, v in phase_s.items()},
         }
         line.update(extra)
     if dist is not None:

@@ -104,7 +104,7 @@ def test_bench_distributed_branch_runs():
     env = _env(_free_port())
     env['DDSPP_BENCH_DIST'] = '1'
     p = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '2', '--warmup', '1',
-                        '--batch', '4', '--no-roofline', '--no-cpu-baseline', '--no-single-stream', '--sustain-seconds', '0.3'],
+                        '--batch', '4', '--full', '--no-roofline', '--no-cpu-baseline', '--no-single-stream', '--sustain-seconds', '0.3'],
                        env=env, capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert p.returncode == 0, p.stderr[-3000:]
     line = json.loads(p.stdout.strip().splitlines()[-1])        # the JSON line must be the LAST line
@@ -113,6 +113,34 @@ def test_bench_distributed_branch_runs():
     assert len(line['per_rank']['ms_step_with_sync_gather']) == 1 and line['per_rank']['ms_step_compute_only'][0] > 0
     assert set(line['gather_hidden']) >= {'compute_only_ms', 'with_synchronous_gather_ms', 'pipelined_ms', 'hidden'}
     assert line['sustained']['n'] >= 200 and line['sustained']['ms_per_step'] > 0 and 'gpu' in line['sustained']
+
+
+def test_bench_plain_run_times_the_steps_and_dumps_the_same_outputs_twice(tmp_path):
+    """`python bench.py --steps K --warmup W --dump-outputs DIR` at the headline size: the line holds the headline and
+    nothing measured besides it; DIR holds what the last timed step returned (a seeded sample: the full dictionary is
+    larger than 64 MB), and a second run with the same arguments writes the same bits."""
+    lines = []
+    for i in range(2):
+        p = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '3', '--warmup', '1',
+                            '--dump-outputs', str(tmp_path / f'run{i}')], capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert p.returncode == 0, p.stderr[-3000:]
+        lines.append(json.loads(p.stdout.strip().splitlines()[-1]))
+    line = lines[0]
+    assert line['steps'] == 3 and line['step_ms']['n'] == 3 and line['step_ms']['median'] > 0
+    assert line['ms_per_step'] == pytest.approx(line['step_ms']['median'], rel=1e-12)      # (median s) x 1e3, rounded
+    assert line['unit'] == 'audio samples/s' and line['higher_is_better'] is True and line['dtype'] == 'f32'
+    assert line['full'] is False and line['extras'] == 'none'
+    assert line['roofline'] is None and line['cpu_baseline'] is None and 'pipelined' not in line and 'sustained' not in line
+    index = line['dump_outputs']['arrays']
+    assert index == lines[1]['dump_outputs']['arrays'] and index['signal']['shape'] == [64, 72000]
+    assert all(v['sampled'] for v in index.values())
+    files = sorted(os.listdir(tmp_path / 'run0'))
+    assert files == sorted(f'{k}.npy' for k in index) and sorted(os.listdir(tmp_path / 'run1')) == files
+    assert sum(os.path.getsize(tmp_path / 'run0' / f) for f in files) <= 64 * 10 ** 6
+    for f in files:
+        x, y = np.load(tmp_path / 'run0' / f), np.load(tmp_path / 'run1' / f)
+        assert x.dtype in (np.float32, np.float64) and np.isfinite(x).all(), f
+        assert np.array_equal(x, y), f          # seeded inputs, no atomics in the kernels: the same bits every run
 
 
 _WORKER2 = r"""
@@ -199,7 +227,7 @@ def test_bench_two_rank_launcher_flow_on_one_gpu():
         env.pop(k, None)
     env.update({'HSA_ENABLE_IPC_MODE_LEGACY': '0', 'DDSPP_BENCH_SHARE_GPU': '1', 'DDSPP_BENCH_BACKEND': 'gloo'})
     p = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '3', '--warmup', '1',
-                        '--batch', '4', '--no-roofline', '--no-cpu-baseline', '--no-extras', '--sustain-seconds', '0.2'],
+                        '--batch', '4', '--full', '--no-roofline', '--no-cpu-baseline', '--no-extras', '--sustain-seconds', '0.2'],
                        env=env, capture_output=True, text=True, timeout=1200, cwd=ROOT)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [l for l in p.stdout.strip().splitlines() if l.startswith('{')]
@@ -284,7 +312,7 @@ def test_bench_eight_rank_launcher_flow_on_one_gpu():
         env.pop(k, None)
     env.update({'HSA_ENABLE_IPC_MODE_LEGACY': '0', 'DDSPP_BENCH_SHARE_GPU': '1', 'DDSPP_BENCH_BACKEND': 'gloo'})
     p = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '8', '--steps', '2', '--warmup', '1',
-                        '--batch', '2', '--seconds', '1', '--no-roofline', '--no-cpu-baseline', '--no-extras', '--sustain-seconds', '0'],
+                        '--batch', '2', '--seconds', '1', '--full', '--no-roofline', '--no-cpu-baseline', '--no-extras', '--sustain-seconds', '0'],
                        env=env, capture_output=True, text=True, timeout=1800, cwd=ROOT)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [l for l in p.stdout.strip().splitlines() if l.startswith('{')]

@@ -319,6 +319,45 @@ def test_bench_extras_levels_and_gpu_sampler_without_a_gpu():
     assert bench.ms_summary([1.0, 3.0, 2.0]) == {'median': 2.0, 'min': 1.0, 'max': 3.0, 'n': 3}
 
 
+def test_bench_dump_outputs_names_bounds_and_repeats(tmp_path):
+    """--dump-outputs: the arrays a caller of the timed call gets (not the echoed inputs, each array once), as float32 /
+    float64 .npy files; over the byte budget every array is cut to the same seeded sample, the same from run to run; a
+    plain run (no --full) measures nothing but the headline steps."""
+    import importlib
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    if root not in sys.path:
+        sys.path.insert(0, root)
+    bench = importlib.import_module('bench')
+    a = bench.parse([])
+    assert not a.full and a.dump_outputs is None
+    assert bench.parse(['--full', '--dump-outputs', 'd']).full and bench.parse(['--dump-outputs', 'd']).dump_outputs == 'd'
+    g = torch.Generator().manual_seed(0)
+    feats = {'f0_hz_0': torch.rand(4, 10, 1, generator=g), 'magnitudes_0': torch.rand(4, 10, 3, generator=g)}
+    sig, dry = torch.rand(4, 300, generator=g), torch.rand(4, 300, generator=g)
+    res = {'signal': sig, 'controls': {'inputs': feats, **feats, 'add': {'signal': dry, 'controls': {'signal_0': sig}},
+                                       'additive': {'signal': dry[:, :100], 'controls': {'shift': torch.arange(4)}},
+                                       'out': {'signal': sig}}}
+    arrays = bench.caller_arrays(res, feats)
+    assert list(arrays) == ['signal', 'controls.add.signal', 'controls.additive.signal', 'controls.additive.controls.shift']
+    assert list(bench.caller_arrays(sig, feats)) == ['signal']
+    idx = bench.dump_outputs(arrays, str(tmp_path / 'all'))
+    assert all(v['sampled'] is None for v in idx.values())
+    assert np.array_equal(np.load(tmp_path / 'all' / 'signal.npy'), sig.numpy())
+    shift = np.load(tmp_path / 'all' / 'controls.additive.controls.shift.npy')
+    assert shift.dtype == np.float64 and np.array_equal(shift, [0, 1, 2, 3])
+    budget = 2000                                        # bytes: a quarter of what the four arrays hold
+    runs = [bench.dump_outputs(arrays, str(tmp_path / f'cut{i}'), budget=budget) for i in range(2)]
+    assert runs[0] == runs[1] and runs[0]['signal'] == {'shape': [4, 300], 'sampled': 1200 * budget // 11232}
+    total = 0
+    for name, v in runs[0].items():
+        x, y = np.load(tmp_path / 'cut0' / f'{name}.npy'), np.load(tmp_path / 'cut1' / f'{name}.npy')
+        assert np.array_equal(x, y) and x.dtype in (np.float32, np.float64) and x.size == v['sampled']
+        total += x.nbytes
+    assert total <= budget
+    assert set(np.load(tmp_path / 'cut0' / 'signal.npy')) <= set(sig.numpy().ravel())
+
+
 def test_plan_cache_is_bounded_and_respects_pins(monkeypatch):
     """rocFFT plans are library-owned handles: the cache destroys the least recently used ones when it is full, never a
     plan pinned by an unfinished two-phase convolution, and clear() (atexit) tolerates a library that is gone."""

@@ -1,13 +1,13 @@
 #!/bin/bash
-# Round-4 profile on the GPU box: kernel-trace stats of bench.py (default command) with the JSON line printed inside that
+# Round-4 profile on the GPU box: kernel-trace stats of bench.py --full with the JSON line printed inside that
 # run, SQ / HBM counters of the step's kernels (tools/step_pmc.sh -> step_valu.json), HBM counters of the graded kernel
 # (-> osc_traffic.json, both carry the hash of the kernel sources), the FilteredNoise kernel alone (tools/noise_pmc.sh).
-set -u
+set -eu          # the first step that fails, faults or times out ends the script: nothing more starts on the card
 cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
 OUT=$R/gpurun_out/prof_r04
 mkdir -p $OUT
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kt -o bench -- python $R/bench.py --steps 10 --warmup 2 > $OUT/bench_under_rocprof.log 2>&1
+timeout -k 10 900 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kt -o bench -- python $R/bench.py --full --steps 10 --warmup 2 > $OUT/bench_under_rocprof.log 2>&1
 grep "^{\"metric" $OUT/bench_under_rocprof.log > $OUT/bench_under_rocprof.json
 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT/pmc_fetch -o p -- python $R/tools/bench_kernels.py --which osc --spans 1 --reps 2 > $OUT/pmc_fetch.log 2>&1
 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $OUT/pmc_write -o p -- python $R/tools/bench_kernels.py --which osc --spans 1 --reps 2 > $OUT/pmc_write.log 2>&1
@@ -23,7 +23,7 @@ bash tools/noise_pmc.sh prof_r04_noise 8 > /dev/null 2>&1
 cp gpurun_out/prof_r04_noise/summary.txt $OUT/noise_pmc.txt
 # the bench line with the fresh counters in place
 cp $OUT/step_valu.json $OUT/osc_traffic.json profiles/
-python bench.py > $OUT/bench.json 2> $OUT/bench.err
+timeout -k 10 600 python bench.py --full > $OUT/bench.json 2> $OUT/bench.err
 find $OUT -name "*.csv" ! -name "bench_kernel_stats.csv" -delete
 ls $OUT
 # round 4: what the chip sustains in float32 multiply-adds, the walk of the FilteredNoise kernel alone, socket power

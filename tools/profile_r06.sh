@@ -1,13 +1,13 @@
 #!/bin/bash
-# Round-6 profile on the GPU box, ONE pass on the final tree: kernel-trace stats of bench.py (default command) with the JSON line
+# Round-6 profile on the GPU box, ONE pass on the final tree: kernel-trace stats of bench.py --full with the JSON line
 # printed inside that run, HBM counters of the graded kernel (-> osc_traffic.json), SQ / HBM counters of the step's kernels
 # (tools/step_pmc.sh -> step_valu.json), the graded kernel in eight processes (placement spread), the round's probes.
-set -u
+set -eu          # the first step that fails, faults or times out ends the script: nothing more starts on the card
 cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
 OUT=$R/gpurun_out/prof_r06
 mkdir -p $OUT
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kt -o bench -- python $R/bench.py --steps 10 --warmup 2 --sustain-seconds 1 > $OUT/bench_under_rocprof.log 2>&1
+timeout -k 10 900 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kt -o bench -- python $R/bench.py --full --steps 10 --warmup 2 --sustain-seconds 1 > $OUT/bench_under_rocprof.log 2>&1
 grep "^{\"metric" $OUT/bench_under_rocprof.log > $OUT/bench_under_rocprof.json
 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT/pmc_fetch -o p -- python $R/tools/bench_kernels.py --which osc --spans 1 --reps 2 > $OUT/pmc_fetch.log 2>&1
 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $OUT/pmc_write -o p -- python $R/tools/bench_kernels.py --which osc --spans 1 --reps 2 > $OUT/pmc_write.log 2>&1
@@ -25,7 +25,7 @@ cp gpurun_out/step_pmc_r06/step_valu.json $OUT/step_valu.json
 cp $(find $OUT/kt -name '*kernel_stats.csv' | head -1) $OUT/bench_kernel_stats.csv
 # the bench line with the fresh counters in place
 cp $OUT/step_valu.json $OUT/osc_traffic.json profiles/
-python bench.py > $OUT/bench.json 2> $OUT/bench.err
+timeout -k 10 600 python bench.py --full > $OUT/bench.json 2> $OUT/bench.err
 find $OUT -name "*.csv" ! -name "bench_kernel_stats.csv" -delete
 # the graded kernel, old and new, in eight processes one after the other: the placement lottery (DESIGN_LOG 4a)
 for i in 1 2 3 4 5 6 7 8; do
